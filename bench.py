@@ -35,6 +35,10 @@ Checks outside the timed region: `parity_in_run` (the HIP path's records == the 
 captures at N = 1; cfg #5 at every N -- every rank's oracle records gathered to rank 0), `frames_lost_vs_sequential` with
 `fidelity_modes` for the 802.15.4 lines (the default lanes + frame repair against ONE sequential lane per channel, the
 reference's receiver).  `frac` prices the dominant kernel's event duration, `step_frac` the whole step.
+
+`--dump-outputs DIR` (rank 0) writes the records the timed path handed its caller in the LAST timed step -- rank 0's
+gathered records at N > 1, both scans' for cfg5 -- as DIR/<name>_<field>.npy (see dump_outputs), so that two builds can be
+compared output for output: the captures depend on the arguments alone (seeded tiles and noise).
 """
 from __future__ import annotations
 
@@ -355,6 +359,48 @@ def parity_in_run(x_dev, workload: str, n_sample: int, device, fmt: int, want=No
 FIDELITY_SHAPES = ((16384, 8192),)      # lane shapes reported beside the default one (fidelity_modes)
 
 
+# ------------------------------------------------------------------------------------------------
+# --dump-outputs: the last timed step's records, for comparing two builds output for output
+# ------------------------------------------------------------------------------------------------
+DUMP_ROW_BYTES = 60_000_000     # .npy payload of all outputs together (the headers come on top: under 64 MB in all)
+DUMP_SEED = 20250101            # the rows kept when an output is larger: the same rows for the same record count
+# the order records are written in: the library's order within a step is not part of its contract (parity_in_run sorts too)
+DUMP_ORDER = ("channel", "sample_index", "len", "proto", "crc_ok", "lqi", "pdu_type", "flags", "aux")
+
+
+def owned_records(parts):
+    """One PKT_DTYPE array that owns its memory, from record arrays or wire-format views into pinned buffers."""
+    from snout_amd import dist as sdist
+    return np.concatenate([np.zeros(0, dtype=_pkt_dtype())] + [sdist.widen_records(np.asarray(p)) for p in parts])
+
+
+def dump_outputs(path: str, outputs: dict) -> dict:
+    """Write every {name: records} as <name>_<field>.npy, float64 [n] (every integer field is exact in it), one per field
+    but the payload, <name>_bytes.npy, float32 [n, 136], and <name>_count.npy, float64 [1]: the records before any
+    sampling.  Rows in DUMP_ORDER.  When the rows of all outputs exceed DUMP_ROW_BYTES, every output keeps the same fixed
+    fraction of its rows, drawn by a generator seeded with DUMP_SEED (kept in DUMP_ORDER)."""
+    dt = _pkt_dtype()
+    fields = [f for f in dt.names if f != "bytes"]
+    row = 8 * len(fields) + 4 * dt["bytes"].shape[0]
+    total = sum(len(r) for r in outputs.values())
+    frac = min(1.0, DUMP_ROW_BYTES / (row * total)) if total else 1.0
+    os.makedirs(path, exist_ok=True)
+    info = {"dir": path, "order": list(DUMP_ORDER), "records": {}, "rows_written": {}}
+    for name, rec in outputs.items():
+        rec = rec[np.lexsort(tuple(rec[f] for f in reversed(DUMP_ORDER)))]
+        n = len(rec)
+        k = n if frac >= 1.0 else int(n * frac)
+        if k < n:
+            rec = rec[np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))]
+        np.save(os.path.join(path, name + "_count.npy"), np.array([n], dtype=np.float64))
+        for f in fields:
+            np.save(os.path.join(path, "%s_%s.npy" % (name, f)), rec[f].astype(np.float64))
+        np.save(os.path.join(path, name + "_bytes.npy"), rec["bytes"].astype(np.float32))
+        info["records"][name] = n
+        info["rows_written"][name] = k
+    return info
+
+
 def lost_vs_sequential(x_dev, workload: str, n_sample: int, device, fmt: int, shapes=()):
     """802.15.4 workloads: the DEFAULT decode (lanes + frame repair) against ONE sequential lane per channel -- the
     reference's receiver (Zigbee_rx/top_block.py:67,69: one clock_recovery_mm_ff / packet_sink loop per channel) -- both on
@@ -438,7 +484,8 @@ def reserved_cus(world: int, fake: int) -> int:
 # one workload on one handle, pipelined submit / collect
 # ------------------------------------------------------------------------------------------------
 def run_workload(name: str, n: int, steps: int, warmup: int, device, rank: int, world: int, fmt: int = 0,
-                 sync: bool = False, gather=None, keep_capture: bool = False, parity_samples: int = 0, checks: bool = True):
+                 sync: bool = False, gather=None, keep_capture: bool = False, parity_samples: int = 0, checks: bool = True,
+                 keep_last: bool = False):
     import torch
     import torch.distributed as dist
     from snout_amd.rx import SnoutRx
@@ -459,12 +506,14 @@ def run_workload(name: str, n: int, steps: int, warmup: int, device, rank: int, 
                  zb_warmup=int(os.environ.get("SNOUT_BENCH_ZB_WARMUP", "0")))        # dev aid: 802.15.4 lane shape (0 = the default rule)
 
     gathered = [0, 0]                   # exchanges finished on rank 0, records in the last one
+    held = [None]                       # rank 0's views of the last exchange (keep_last: copied after the timed steps)
 
     def take_exchange():
         parts = gather.finish(views=True)
         if parts is not None:
             gathered[0] += 1
             gathered[1] = int(sum(len(v) for v in parts))
+            held[0] = parts
 
     def finish_one():
         pk = rx.collect(copy=False)                             # a count when the records stay on the device
@@ -516,11 +565,16 @@ def run_workload(name: str, n: int, steps: int, warmup: int, device, rank: int, 
     gc.collect()
     gc.disable()
     t0 = time.perf_counter()
-    run_steps(steps)
+    last = run_steps(steps)
     drain()                 # every step's records are on rank 0 before the clock stops
     fence()
     dt = time.perf_counter() - t0
     gc.enable()
+    # keep_last: the records the caller got from the last timed step (rank 0's gathered ones with an exchange attached),
+    # copied before the next submit or exchange reuses the buffers behind them
+    last_records = None
+    if keep_last:
+        last_records = owned_records([last]) if gather is None else (owned_records(held[0]) if held[0] is not None else None)
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=device if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -577,6 +631,8 @@ def run_workload(name: str, n: int, steps: int, warmup: int, device, rank: int, 
         if gather.fake:
             res["fake_world"] = gather.fake
         res["reserved_cus"] = rcus
+    if last_records is not None:
+        res["last_records"] = last_records
     rx.close()
     if parity_samples:
         # the whole capture where the oracle finishes it in seconds (first_sample_index 0: rank 0's own capture)
@@ -646,7 +702,8 @@ def traffic_from_profiles(workload: str, kernel: str, n: int):
 # ------------------------------------------------------------------------------------------------
 # cfg #5: both wideband scans concurrently, sharded in 2^24-sample segments
 # ------------------------------------------------------------------------------------------------
-def run_cfg5(steps: int, warmup: int, device, rank: int, world: int, seconds: float = 10.0, group=None, parity: bool = False):
+def run_cfg5(steps: int, warmup: int, device, rank: int, world: int, seconds: float = 10.0, group=None, parity: bool = False,
+             keep_last: bool = False):
     import torch
     import torch.distributed as dist
     from snout_amd import dist as sdist
@@ -776,6 +833,8 @@ def run_cfg5(steps: int, warmup: int, device, rank: int, world: int, seconds: fl
     fence()
     dt = time.perf_counter() - t0
     gc.enable()
+    # keep_last: rank 0's de-duplicated records of the last timed step, copied out of the exchanges' pinned buffers
+    last_records = {"btle": owned_records([results["b"]]), "zigbee": owned_records([results["z"]])} if keep_last and rank == 0 else None
     if trace is not None and rank == 0:
         import collections
         agg, cnt = collections.Counter(), collections.Counter()
@@ -859,6 +918,8 @@ def run_cfg5(steps: int, warmup: int, device, rank: int, world: int, seconds: fl
         if fake:
             res["fake_world"] = {"blocks_on_rank0": fake, "note": "rehearsal at world size 1: rank 0 sorts, de-duplicates and downloads "
                                  "%d copies of its own records per step (sample_index shifted per copy), as it will at N = %d" % (fake, fake)}
+        if last_records is not None:
+            res["last_records"] = last_records
         res["achieved_GBps"] = res["algorithmic_bytes"] / (res["ms_per_step"] * 1e-3) / 1e9
         res["frac"] = res["step_frac"] = res["achieved_GBps"] / HBM_PEAK_GBPS       # (priced on the whole step)
         if want_recs is not None:
@@ -970,7 +1031,12 @@ def main():
     ap.add_argument("--no-others", action="store_true", help="N = 1: skip the other_workloads block")
     ap.add_argument("--sync", action="store_true",
                     help="one segment at a time (no submit/collect pipelining); for profiling")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step (rank 0) as DIR/<name>_<field>.npy, float32 / float64, "
+                         "at most 64 MB in all (a fixed seeded sample of the rows beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself (what replaces the sequential hop of
@@ -1021,12 +1087,13 @@ def main():
     # other_workloads.cfg5 at every N and is the headline with --workload cfg5.
     headline = args.workload or "cfg3"
     out = None
+    dump = {}                                   # --dump-outputs: name -> the last timed step's records (rank 0)
 
-    def cfg5_run(steps, warmup, parity):
+    def cfg5_run(steps, warmup, parity, keep_last=False):
         """cfg #5 with its parity_in_run: on the timed capture itself at N = 1; at N > 1 on a separate pass over 1 s of each
         band per rank (N ranks share the host's cores: the oracle on N x 10 s would take minutes)."""
         full = world == 1 or args.seconds <= 1.0
-        r5 = run_cfg5(steps, warmup, device, rank, world, seconds=args.seconds, parity=parity and full)
+        r5 = run_cfg5(steps, warmup, device, rank, world, seconds=args.seconds, parity=parity and full, keep_last=keep_last)
         if parity and not full:
             rp = run_cfg5(2, 1, device, rank, world, seconds=1.0, parity=True)
             if rank == 0:
@@ -1034,8 +1101,9 @@ def main():
         return r5
 
     if headline == "cfg5":
-        r5 = cfg5_run(args.steps, args.warmup, not args.no_cpu)
+        r5 = cfg5_run(args.steps, args.warmup, not args.no_cpu, keep_last=args.dump_outputs is not None)
         if rank == 0:
+            dump = {k + "_records": v for k, v in r5.pop("last_records", {}).items()}
             out = {"metric": METRIC, "value": r5["value"], "unit": "Msamples/s", "n_gpus": world,
                    "steps": args.steps, "warmup": args.warmup, "ms_per_step": r5["ms_per_step"],
                    "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
@@ -1053,7 +1121,10 @@ def main():
         gather = (sdist.AsyncRecordGather(device, width=WORKLOADS[headline][4], fake_world=fake)
                   if (world > 1 or dist.is_initialized() or fake > 1) else None)
         res, x = run_workload(headline, n, args.steps, args.warmup, device, rank, world, fmt=fmt, sync=args.sync,
-                              gather=gather, keep_capture=True, checks=not args.no_cpu)       # (--no-cpu: profiling runs, no checks)
+                              gather=gather, keep_capture=True, checks=not args.no_cpu,       # (--no-cpu: profiling runs, no checks)
+                              keep_last=args.dump_outputs is not None)
+        if "last_records" in res:
+            dump = {"records": res.pop("last_records")}
         if rank == 0:
             traffic, tsrc = (traffic_from_profiles(headline, res["kernel"], n) if fmt == 0 else (None, None))
             rbest, rmean = read_peak(x, device)
@@ -1120,6 +1191,8 @@ def main():
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()
+    if rank == 0 and args.dump_outputs is not None:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, dump)
     if rank == 0:
         # RCCL prints its version banner through C stdio, which would otherwise be flushed at exit, after the JSON:
         # the JSON is the last line on stdout

@@ -81,3 +81,50 @@ def test_a_capture_cycles_through_distinct_tiles():
     truths = [[0] * (g + 1) for g in range(K)]             # tile g holds g + 1 packets
     assert bench.truth_in(truths, L, 5 * L) == 1 + 2 + 3 + 4 + 1
     assert bench.truth_in(truths, L, 2 * L + 5, first_sample=L - 3) == 2 + 3    # whole tiles 1 and 2
+
+
+def _records(n, seed):
+    import numpy as np
+    from snout_amd._ffi import PKT_DTYPE
+    rng = np.random.default_rng(seed)
+    r = np.zeros(n, dtype=PKT_DTYPE)
+    r["sample_index"] = rng.integers(0, 1 << 40, n, dtype=np.uint64)
+    r["channel"] = rng.integers(0, 40, n)
+    r["len"] = rng.integers(1, 136, n)
+    r["crc_ok"] = rng.integers(0, 2, n)
+    r["aux"] = rng.integers(0, 1 << 32, n, dtype=np.uint64)
+    r["bytes"] = rng.integers(0, 256, (n, 136))
+    return r
+
+
+def test_dump_outputs_writes_every_record_field_exactly(tmp_path):
+    """--dump-outputs: one float64 array per record field, the payload as float32 [n, 136], rows in (channel,
+    sample_index, ...) order whatever order the records came in, every value exact."""
+    import numpy as np
+    rec = _records(500, 1)
+    info = bench.dump_outputs(str(tmp_path), {"records": rec[::-1].copy()})
+    assert info["records"] == {"records": 500} and info["rows_written"] == {"records": 500}
+    want = rec[np.lexsort((rec["len"], rec["sample_index"], rec["channel"]))]
+    for f in bench.DUMP_ORDER:
+        a = np.load(tmp_path / f"records_{f}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, want[f].astype(np.float64)), f
+    b = np.load(tmp_path / "records_bytes.npy")
+    assert b.dtype == np.float32 and b.shape == (500, 136) and np.array_equal(b, want["bytes"])
+    assert np.load(tmp_path / "records_count.npy").tolist() == [500.0]
+    assert all(np.load(p).dtype in (np.float32, np.float64) for p in tmp_path.iterdir())
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_the_limit(tmp_path, monkeypatch):
+    """Above the size limit every output keeps the same fraction of its rows, the same rows on every call."""
+    import numpy as np
+    row = 8 * 9 + 4 * 136
+    monkeypatch.setattr(bench, "DUMP_ROW_BYTES", 300 * row)
+    outs = {"btle_records": _records(400, 2), "zigbee_records": _records(200, 3)}
+    a = bench.dump_outputs(str(tmp_path / "a"), outs)
+    b = bench.dump_outputs(str(tmp_path / "b"), {k: v[::-1].copy() for k, v in outs.items()})
+    assert a["records"] == {"btle_records": 400, "zigbee_records": 200}
+    assert a["rows_written"] == b["rows_written"] == {"btle_records": 200, "zigbee_records": 100}
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) < 300 * row + 32 * 128
+    for p in (tmp_path / "a").iterdir():
+        assert np.array_equal(np.load(p), np.load(tmp_path / "b" / p.name)), p.name
+    assert np.load(tmp_path / "a" / "zigbee_records_count.npy").tolist() == [200.0]
