@@ -47,6 +47,14 @@ extern "C" {
 /* protocols (snout/core/protocols/__init__.py:2-27 names them BTLE / ZIGBEE) */
 #define SNOUT_PROTO_BTLE   0u
 #define SNOUT_PROTO_ZIGBEE 1u
+#define SNOUT_PROTO_ZWAVE  2u   /* Z-Wave R2 (ITU-T G.9959, 40 kbit/s 2-FSK), n_channels = 1: IQ at 800 ksps tuned to the
+                                   channel + 200 kHz (snout/modulations/ZWave/hackrf/ZWave_rx/top_block.py:41-90)    */
+
+/* Z-Wave lane shape (cfg.zb_core / cfg.zb_warmup of a SNOUT_PROTO_ZWAVE handle; 0 -> these): the clock recovery and the
+ * packet sink run in lanes of `core` input samples that start `warmup` samples early.  Records are a function of the
+ * shape; zb_core >= the call's samples is the reference's one sequential receiver. */
+#define SNOUT_ZWAVE_LANE_CORE   32768u
+#define SNOUT_ZWAVE_LANE_WARMUP 16384u
 
 /* input sample formats (snout_rx_cfg.sample_format).  Integer samples stand for the cf32 samples
  * v * 2^-7 (sc8) / v * 2^-15 (sc16): conversion and scale are exact in fp32, so results are bit-
@@ -82,6 +90,8 @@ extern "C" {
 #define SNOUT_STAGE_ZB_DISCRIM    2u  /* a4: quadrature_demod_cf output                        */
 #define SNOUT_STAGE_ZB_DCREMOVED  3u  /* a5: x - single_pole_iir(x)                            */
 #define SNOUT_STAGE_ZB_CHIPS      4u  /* a6: clock_recovery_mm_ff output (lane 0 of channel 0) */
+#define SNOUT_STAGE_ZW_FILTERED   5u  /* Z-Wave z4: the low-pass filtered discriminator, one float per input sample */
+#define SNOUT_STAGE_ZW_SYMBOLS    6u  /* Z-Wave z5: clock_recovery_mm_ff output of lane `channel_slot`, in step order */
 
 typedef struct snout_rx_cfg {
     uint32_t abi_version;     /* SNOUT_ABI_VERSION                                              */
@@ -96,7 +106,9 @@ typedef struct snout_rx_cfg {
     uint32_t access_addr;     /* BTLE `-a` (btle.py:66); 0 -> 0x8E89BED6                         */
     uint32_t crc_init;        /* BTLE `-k` (btle.py:67); 0 -> 0x555555                           */
     uint32_t chip_threshold;  /* packet_sink(threshold) (top_block.py:67); 0 -> 10               */
-    uint32_t zb_core;         /* Zigbee lane core length in channel samples; 0 (with zb_warmup != 0) -> 2048 */
+    uint32_t zb_core;         /* Z-Wave: lane core in input samples, 0 -> SNOUT_ZWAVE_LANE_CORE (>= 1024); zb_warmup likewise
+                                 (0 -> SNOUT_ZWAVE_LANE_WARMUP).
+                                 Zigbee lane core length in channel samples; 0 (with zb_warmup != 0) -> 2048 */
     uint32_t zb_warmup;       /* Zigbee lane warm-up before its core, channel samples; 0 (with zb_core != 0) -> 512;
                                  multiples of 64, warm-up < core; the timing loop needs >= 256.
                                  BOTH 0 (the default): core 6144 / warm-up 3072 for a wideband handle, 6144 / 1024 for a
@@ -128,7 +140,11 @@ typedef struct snout_rx_cfg {
  * receives every frame (frame repair).  Never set with one lane per channel. */
 #define SNOUT_PKT_ZB_REPAIRED 0x08u
 
-/* One decoded packet. Fixed 160 bytes so records can be gathered across ranks as flat bytes. */
+/* One decoded packet. Fixed 160 bytes so records can be gathered across ranks as flat bytes.
+ * Z-Wave (proto 2): sample_index = the clock recovery's input position (window start) of the symbol that carries the
+ * SOF's last bit, plus first_sample_index; channel = cfg.channel (a label); len = L, the MPDU length byte (10..64);
+ * bytes = the MPDU from HomeID through the checksum; crc_ok = (0xFF ^ b[0] ^ ... ^ b[L-2]) == b[L-1];
+ * pdu_type = header type, FrameCtrl[0] & 0x0F (bytes[5]); lqi = flags = 0; aux = lane id.  Ordered by sample_index. */
 typedef struct snout_pkt {
     uint64_t sample_index;    /* BTLE: first sample of the access address; Zigbee: window start of the
                                  chip 319 chips before the one that completes the SFD, i.e. the first

@@ -18,7 +18,8 @@ from . import synth
 from .scan import ArraySource, BtleScan, FileSource, StreamSource, WidebandSource, ZigbeeScan
 
 DEFAULTS = {"btle": dict(channels=(0, 39), default=37, timeout=10),      # snout/util/__init__.py:4-17
-            "zigbee": dict(channels=(11, 26), default=11, timeout=10)}
+            "zigbee": dict(channels=(11, 26), default=11, timeout=10),
+            "zwave": dict(channels=(), default=None, timeout=10)}
 
 
 def parse_channels(spec, proto: str):
@@ -223,6 +224,53 @@ def zigbee_scan(channels, active, packets, timeout, wideband, sharded, segment, 
     if filename:
         from .formats import write_pcap
         write_pcap(filename, [(m.timestamp, m.mpdu) for m in msgs])
+    click.echo(f"{len(msgs)} frames", err=True)
+
+
+@main.group()
+def zwave():
+    """Z-Wave R2 (ITU-T G.9959, 40 kbit/s), one channel at 800 ksps."""
+
+
+@zwave.command("scan")
+@click.option("-c", "--channel", "mhz", type=float, default=None,
+              help="channel frequency in MHz, a label for the output (default 908.4); the capture is tuned to it + 200 kHz")
+@click.option("-a", "--active", is_flag=True, default=None, help="Active Scan (accepted; the receive path is passive)")
+@click.option("-n", "--num", "packets", type=int, default=None, help="Number of packets to scan for")
+@click.option("-t", "--timeout", type=float, default=None, help="Add a timeout restriction (in seconds).")
+@click.option("-f", "--filename", default=None, help="pcap dump file (LINKTYPE_ZWAVE_R1_R2)")
+@click.option("--iq", callback=_iq_path, default=None,
+              help="capture file at 800 ksps; '-' (stdin) or a FIFO: a live stream, read in overlapping segments, -t by the wall clock")
+@click.option("--format", "fmt", type=click.Choice(sorted(FORMATS)), default="cf32",
+              help="sample format of --iq: cf32, sc8 (hackrf_transfer int8), sc16")
+@click.option("--synthetic", is_flag=True, help="generate a synthetic capture")
+@click.option("--seconds", type=float, default=0.25, help="length of a synthetic capture")
+@click.option("--lane-core", type=int, default=0, help="clock-recovery lane length in input samples (0: SNOUT_ZWAVE_LANE_CORE); "
+              "a lane at least as long as the capture is the reference's one sequential loop")
+@click.option("--lane-warmup", type=int, default=0, help="samples a lane starts before its core (0: SNOUT_ZWAVE_LANE_WARMUP)")
+def zwave_scan(mhz, active, packets, timeout, filename, iq, fmt, synthetic, seconds, lane_core, lane_warmup):
+    """One line per frame with a good checksum: time, MHz, HomeID, source, destination, header type, sequence
+    number, length, MPDU hex."""
+    from . import zwave as zw
+    mhz = zw.DEFAULT_MHZ if mhz is None else mhz
+    packets, timeout = stop_conditions("zwave", packets, timeout)
+    if iq:
+        src = _file_or_stream(iq, FORMATS[fmt])
+    elif synthetic:
+        x, _ = zw.capture(int(seconds * zw.FS), seed=1)
+        if fmt != "cf32":
+            x = synth.quantize(x, FORMATS[fmt]).reshape(-1, 2)
+        src = ArraySource({0: x})
+        src.sample_format = FORMATS[fmt]
+    else:
+        raise click.UsageError("give --iq FILE or --synthetic (no live SDR in this build)")
+    rx_kw = dict(zb_core=lane_core, zb_warmup=lane_warmup) if (lane_core or lane_warmup) else {}
+    scan = zw.ZWaveScan(source=src, mhz=mhz, timeout=timeout, packet_threshold=packets, rx_kw=rx_kw)
+    scan.events.on("zwave.packet-received", lambda message: click.echo(message.line()))
+    msgs = scan.run()
+    if filename:
+        from .formats import write_pcap
+        write_pcap(filename, [(m.timestamp, m.mpdu) for m in msgs], linktype=zw.LINKTYPE_ZWAVE_R1_R2)
     click.echo(f"{len(msgs)} frames", err=True)
 
 

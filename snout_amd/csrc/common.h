@@ -251,4 +251,19 @@ struct ZbCtx {
     int soft(uint32_t stage_id, uint32_t lane, uint64_t n, float* out, uint64_t cap, uint64_t* n_out);
 };
 
+// Z-Wave R2 pipeline state (zwave.hip): one narrowband channel at 800 ksps.
+struct ZwCtx {
+    uint32_t core = SNOUT_ZWAVE_LANE_CORE, warmup = SNOUT_ZWAVE_LANE_WARMUP, channel = 0;
+    uint32_t K = 16;                 // record slots per lane (grows on overflow)
+    uint32_t n_lanes = 0;            // lanes of the last enqueued segment
+    uint64_t first_index = 0;
+    DevBuf d_atan, d_mmse, d_f, d_stage, d_cnt, d_soft;    // d_f: z4 output, one f32 per input sample; d_cnt: counts | offsets
+    int init(uint32_t core, uint32_t warmup, uint32_t channel);
+    void destroy();
+    int enqueue_front(const void* d_iq, uint64_t n, int fmt, hipStream_t st, ResultSlot& s);   // zw_front between ev_k0 / ev_k1
+    int enqueue_tail(uint64_t n, uint64_t first, hipStream_t st, ResultSlot& s);             // lanes, ordered records, totals
+    bool check_overflow(const ResultSlot& s);
+    int soft(uint32_t stage_id, uint32_t lane, uint64_t n, float* out, uint64_t cap, uint64_t* n_out);
+};
+
 }  // namespace snout

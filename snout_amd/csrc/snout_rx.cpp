@@ -108,6 +108,7 @@ struct snout_rx {
     int n_tails = 1;          // tail streams CREATED (SNOUT_TAIL_STREAMS overrides): work set k's tail runs on stream k % n_tails
     bool sync_call = false;   // inside snout_rx_process*: nothing to overlap, the tail stays on the caller's stream
     ZbCtx zb;
+    ZwCtx zw, zw2, zw3;       // Z-Wave work sets (as the narrowband 802.15.4 ones)
     PfbCtx pfb;
     DevBuf d_iq;              // staging for snout_rx_process (host input)
     static constexpr int kSlots = 3;    // segments in flight: front end i+1 is queued before copy i-1 lands
@@ -137,6 +138,7 @@ static BtleCtx& btle_of(snout_rx* h, const ResultSlot& s)
     return s.work_set == 0 ? h->btle : (s.work_set == 1 ? h->btle2 : h->btle3);
 }
 static ZbCtx& zb_of(snout_rx* h, const ResultSlot& s) { return s.work_set == 0 ? h->zb : (s.work_set == 1 ? h->zb2 : h->zb3); }
+static ZwCtx& zw_of(snout_rx* h, const ResultSlot& s) { return s.work_set == 0 ? h->zw : (s.work_set == 1 ? h->zw2 : h->zw3); }
 
 // Enqueue every kernel of one segment, results into slot s.  No host synchronisation.
 // BTLE: the front end (demod+correlate, or channelizer+correlate) runs on the caller's stream `st`;
@@ -201,6 +203,18 @@ static int enqueue_segment(snout_rx* h, ResultSlot& s, hipStream_t st)
         ch_iq = (fused_zb && n_ch >= 9u) ? nullptr : h->pfb.d_y.as<float>();
         ch_stride = h->pfb.y_stride;
     }
+    if (h->cfg.proto == SNOUT_PROTO_ZWAVE) {
+        // zw_front (the dominant kernel, between ev_k0 / ev_k1) on the caller's stream; the lanes and the ordered records on
+        // the work set's tail stream, beside the next segment's zw_front
+        ZwCtx& z = zw_of(h, s);
+        if (int rc = z.enqueue_front(s.iq, s.n_in, ch_fmt, st, s)) return rc;
+        SNOUT_HIP(hipEventRecord(s.ev_front, st));
+        if (!inline_tail) SNOUT_HIP(hipStreamWaitEvent(tail, s.ev_front, 0));
+        if (int rc = z.enqueue_tail(s.n_in, s.first_index, tail, s)) return rc;
+        SNOUT_HIP(hipEventRecord(s.ev_compute, tail));
+        SNOUT_HIP(hipEventRecord(h->ws_free[s.work_set], tail));
+        return 0;
+    }
     if (h->cfg.proto == SNOUT_PROTO_BTLE) {
         BtleCtx& b = btle_of(h, s);
         if (int rc = b.reserve(n_ch, s.segs.count)) return rc;
@@ -262,7 +276,8 @@ static int finish_slot(snout_rx* h, ResultSlot& s)
     for (int attempt = 0; attempt < 12; attempt++) {
         SNOUT_HIP(hipEventSynchronize(s.ev_copy));
         const bool over = h->cfg.proto == SNOUT_PROTO_BTLE ? btle_of(h, s).check_overflow(s)
-                                                           : zb_of(h, s).check_overflow(s);
+                          : h->cfg.proto == SNOUT_PROTO_ZWAVE ? zw_of(h, s).check_overflow(s)
+                                                              : zb_of(h, s).check_overflow(s);
         if (!over) { s.n_pkts = s.h_totals[1]; return SNOUT_OK; }
         // other segments in flight share this slot's work set every second submit: let them finish
         // (their results are already on their way to their own slots) before reusing it
@@ -338,6 +353,10 @@ int snout_rx_create(const snout_rx_cfg* cfg, snout_rx** out)
     if (c.crc_init == 0) c.crc_init = 0x555555u;
     if (c.chip_threshold == 0) c.chip_threshold = 10;
     if (c.taps_per_branch == 0) c.taps_per_branch = 16;
+    if (c.proto == SNOUT_PROTO_ZWAVE) {       // its own lane shape (input samples at 800 ksps)
+        if (c.zb_core == 0) c.zb_core = SNOUT_ZWAVE_LANE_CORE;
+        if (c.zb_warmup == 0) c.zb_warmup = SNOUT_ZWAVE_LANE_WARMUP;
+    }
     if (c.zb_core == 0 && c.zb_warmup == 0) snout_zigbee_lane_shape(c.n_channels, &c.zb_core, &c.zb_warmup);   // the default shape, fixed per handle (by its kind: n_channels is defaulted below, 0 = narrowband)
     if (c.zb_core == 0) c.zb_core = 2048;
     if (c.zb_warmup == 0) c.zb_warmup = 512;
@@ -355,7 +374,17 @@ int snout_rx_create(const snout_rx_cfg* cfg, snout_rx** out)
         set_last_error("zb_core %u / zb_warmup %u out of range", c.zb_core, c.zb_warmup);
         goto fail;
     }
-    if (c.proto == SNOUT_PROTO_BTLE && c.n_channels == 1) {
+    if (c.proto == SNOUT_PROTO_ZWAVE) {
+        if (c.n_channels != 1 || c.zb_core < 1024 || c.zb_warmup > (1u << 24)) {
+            set_last_error("Z-Wave: n_channels %u (1 only), lane core %u (>= 1024), warm-up %u (<= 2^24)",
+                           c.n_channels, c.zb_core, c.zb_warmup);
+            goto fail;
+        }
+        rc = h->zw.init(c.zb_core, c.zb_warmup, c.channel);
+        if (!rc) rc = h->zw2.init(c.zb_core, c.zb_warmup, c.channel);
+        if (!rc) rc = h->zw3.init(c.zb_core, c.zb_warmup, c.channel);
+        if (rc) goto fail;
+    } else if (c.proto == SNOUT_PROTO_BTLE && c.n_channels == 1) {
         if (c.channel > 39) { set_last_error("BTLE channel %u", c.channel); goto fail; }
         uint16_t ch = (uint16_t)c.channel;
         rc = h->btle.init(1, &ch, c.access_addr, c.crc_init, c.max_hits);
@@ -403,7 +432,7 @@ int snout_rx_create(const snout_rx_cfg* cfg, snout_rx** out)
     // discriminator, and consecutive segments' lanes overlap each other only on separate streams (1e9 samples: 4.05 ms
     // per step with three, 5.2 with one).
     if (const char* e = getenv("SNOUT_EXT_LAUNCH")) h->ext_launch = atoi(e) != 0;
-    h->n_tails = (c.proto == SNOUT_PROTO_ZIGBEE && !h->wide) ? 3 : 1;
+    h->n_tails = ((c.proto == SNOUT_PROTO_ZIGBEE || c.proto == SNOUT_PROTO_ZWAVE) && !h->wide) ? 3 : 1;
     if (const char* e = getenv("SNOUT_TAIL_STREAMS")) { const int v = atoi(e); if (v >= 1 && v <= 3) h->n_tails = v; }
     for (auto& s : h->slots) { rc = s.init(); if (rc) goto fail; }
     for (int k = 0; k < 3; k++) {
@@ -450,6 +479,9 @@ void snout_rx_destroy(snout_rx* h)
     h->zb.destroy();
     h->zb2.destroy();
     h->zb3.destroy();
+    h->zw.destroy();
+    h->zw2.destroy();
+    h->zw3.destroy();
     h->pfb.destroy();
     h->d_iq.release();
     for (auto& s : h->slots) s.destroy();
@@ -734,6 +766,8 @@ int snout_rx_profile(snout_rx* h, snout_rx_prof* out)
             case PfbCtx::kKernelValu: snprintf(out->dominant_name, sizeof(out->dominant_name), "pfb_channelize<%u>", h->pfb.M); break;
             default: snprintf(out->dominant_name, sizeof(out->dominant_name), "pfb_spec%u", h->pfb.M); break;
         }
+    } else if (h->cfg.proto == SNOUT_PROTO_ZWAVE) {
+        snprintf(out->dominant_name, sizeof(out->dominant_name), "zw_front");
     } else if (h->cfg.proto == SNOUT_PROTO_ZIGBEE) {
         out->dominant_launches = 2;
         snprintf(out->dominant_name, sizeof(out->dominant_name), "zb_discrim..zb_walk");
@@ -791,6 +825,10 @@ int snout_rx_soft(snout_rx* h, uint32_t stage, uint32_t channel_slot, float* out
             out[n] = (float)((pl[g * 4u + j] >> l) & 1ull);
         }
         return nb > cap ? SNOUT_EOVERFLOW : SNOUT_OK;
+    }
+    if (h->cfg.proto == SNOUT_PROTO_ZWAVE && (stage == SNOUT_STAGE_ZW_FILTERED || stage == SNOUT_STAGE_ZW_SYMBOLS)) {
+        if (h->last_nch < 9) return SNOUT_EINVAL;
+        return zw_of(h, *h->last).soft(stage, channel_slot, h->last_nch, out, cap, n_out);
     }
     if (h->cfg.proto == SNOUT_PROTO_ZIGBEE && stage >= SNOUT_STAGE_ZB_DISCRIM &&
         stage <= SNOUT_STAGE_ZB_CHIPS) {

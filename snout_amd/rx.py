@@ -8,7 +8,7 @@ from typing import Optional
 import numpy as np
 
 from . import _ffi
-from ._ffi import PKT_DTYPE, PROTO_BTLE, PROTO_ZIGBEE, SnoutError  # noqa: F401
+from ._ffi import PKT_DTYPE, PROTO_BTLE, PROTO_ZIGBEE, PROTO_ZWAVE, SnoutError  # noqa: F401
 
 
 @dataclass
@@ -30,13 +30,15 @@ class SnoutRx:
     (dtype :data:`PKT_DTYPE`). ``iq`` may be a numpy complex64/float32 array (host path,
     PCIe-inclusive) or a torch CUDA tensor / (device pointer, n) pair (HBM-resident path)."""
 
-    def __init__(self, proto: int = PROTO_BTLE, channel: int = 37, n_channels: int = 1,
+    def __init__(self, proto: int = PROTO_BTLE, channel: Optional[int] = None, n_channels: int = 1,
                  access_addr: int = 0, crc_init: int = 0, chip_threshold: int = 0,
                  taps_per_branch: int = 0, zb_core: int = 0, zb_warmup: int = 0,
                  max_hits: int = 0, device: int = -1, keep_channel_iq: bool = False,
                  sample_format: int = 0, batch_segments: int = 1, records_on_device: bool = False,
                  reserved_cus: int = 0):
         self._lib = _ffi.load()
+        if channel is None:                  # BTLE channel 37; a Z-Wave handle's channel is a label, 0 by default
+            channel = 0 if proto == PROTO_ZWAVE else 37
         cfg = _ffi.RxCfg(abi_version=_ffi.ABI_VERSION, proto=proto, n_channels=n_channels,
                          taps_per_branch=taps_per_branch, channel=channel,
                          access_addr=access_addr, crc_init=crc_init,

@@ -101,8 +101,12 @@ class StreamSource(IqSource):
         bps = {0: 8, 1: 2, 2: 4}[self.sample_format]
         np_dt = {0: np.float32, 1: np.int8, 2: np.int16}[self.sample_format]
         zb = proto == _ffi.PROTO_ZIGBEE
+        zw = proto == _ffi.PROTO_ZWAVE
         overlap = ZIGBEE_OVERLAP if zb else BTLE_OVERLAP
         preroll = 4 * 6250 if zb else 0            # sharded.ZIGBEE_PREROLL_CH: the DC estimate restarts with every segment
+        if zw:                                      # Z-Wave: the longest frame; a pre-roll of the lane warm-up and the FIR halos
+            from . import zwave
+            overlap, preroll = zwave.OVERLAP - zwave.PREROLL, zwave.PREROLL
         seg = max(self.segment, 4 * (overlap + preroll))
         dev = torch.device("cuda", torch.cuda.current_device() if device < 0 else device)
         rx = SnoutRx(proto=proto, channel=channel, device=device, sample_format=self.sample_format, **rx_kw)
@@ -122,9 +126,10 @@ class StreamSource(IqSource):
                 si = int(p["sample_index"])
                 if si < own_from:
                     continue
-                if zb:
+                if zb or zw:
                     body = bytes(p["bytes"][:p["len"]])
-                    if any(abs(si - s0) <= 8 * 64 + 8 and body == b0 for s0, b0 in recent):
+                    tol = 2 * 20 if zw else 8 * 64 + 8      # Z-Wave: zwave.DEDUP_TOL, two symbols
+                    if any(abs(si - s0) <= tol and body == b0 for s0, b0 in recent):
                         continue
                     now.append((si, body))
                 else:
@@ -132,7 +137,7 @@ class StreamSource(IqSource):
                         continue
                     seen_until = si
                 keep.append(i)
-            if zb:
+            if zb or zw:
                 recent = now
             return rec[keep]
         try:
