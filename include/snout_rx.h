@@ -102,7 +102,8 @@ typedef struct snout_rx_cfg {
     uint32_t taps_per_branch; /* P of the PFB prototype (M*P taps); 0 -> 16                     */
     uint32_t channel;         /* n_channels==1: protocol channel number of the input
                                  (BTLE 0..39 -> whitening seed, `-c` of btle.py:64;
-                                  Zigbee 11..26, top_block.py:94-96). Ignored for wideband.     */
+                                  Zigbee 11..26, top_block.py:94-96; Z-Wave: a label 0..0xFFFF
+                                  copied to the records). Ignored for wideband.                 */
     uint32_t access_addr;     /* BTLE `-a` (btle.py:66); 0 -> 0x8E89BED6                         */
     uint32_t crc_init;        /* BTLE `-k` (btle.py:67); 0 -> 0x555555                           */
     uint32_t chip_threshold;  /* packet_sink(threshold) (top_block.py:67); 0 -> 10               */

@@ -375,9 +375,9 @@ int snout_rx_create(const snout_rx_cfg* cfg, snout_rx** out)
         goto fail;
     }
     if (c.proto == SNOUT_PROTO_ZWAVE) {
-        if (c.n_channels != 1 || c.zb_core < 1024 || c.zb_warmup > (1u << 24)) {
-            set_last_error("Z-Wave: n_channels %u (1 only), lane core %u (>= 1024), warm-up %u (<= 2^24)",
-                           c.n_channels, c.zb_core, c.zb_warmup);
+        if (c.n_channels != 1 || c.zb_core < 1024 || c.zb_warmup > (1u << 24) || c.channel > 0xFFFFu) {
+            set_last_error("Z-Wave: n_channels %u (1 only), lane core %u (>= 1024), warm-up %u (<= 2^24), "
+                           "channel %u (<= 0xFFFF: the record's label)", c.n_channels, c.zb_core, c.zb_warmup, c.channel);
             goto fail;
         }
         rc = h->zw.init(c.zb_core, c.zb_warmup, c.channel);

@@ -26,6 +26,9 @@ def _captures(kind, sizes):
             x, _ = synth.btle_capture(n, seed=60 + i, mean_gap=3000.0)
         elif kind == "zigbee":
             x, _ = synth.zigbee_capture(n, seed=60 + i, mean_gap=5000.0)
+        elif kind == "zwave":
+            from snout_amd import zwave
+            x, _ = zwave.capture(max(n, 1), seed=60 + i, mean_gap=3000.0)
         elif kind == "btle40":
             x, _ = synth.wideband_capture(0, n, seed=60 + i, bins=[3, 17, 33], mean_gap=4000.0)
         else:
@@ -39,6 +42,7 @@ def _captures(kind, sizes):
     ("zigbee", dict(proto=1, channel=11), [1 << 16, 1 << 19, 3000, 1 << 18, 77, 1 << 19, 1 << 14]),
     ("btle40", dict(proto=0, n_channels=40), [40 * 3000, 40 * 20000, 700, 40 * 9000, 40 * 20000]),
     ("zigbee16", dict(proto=1, n_channels=16), [16 * 9000, 16 * 40000, 300, 16 * 20000, 16 * 40000]),
+    ("zwave", dict(proto=2), [1 << 16, (1 << 19) + 5, 3001, 1 << 18, 7, (1 << 19) + 3, (1 << 14) + 1]),
 ])
 def test_sizes_change_while_segments_are_in_flight(kind, kw, sizes):
     import torch
